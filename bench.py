@@ -9,7 +9,11 @@ kernels are built in (see `ba` in the output) -- by one Gauss-Newton iteration o
 adjustment (linearise + Schur + reduce + solve + back-substitute) on the same landmarks.
 Inputs are resident in HBM before the timed region.  `value` = landmarks (all ranks) / step.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--landmarks L] [--cams C]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--landmarks L] [--cams C] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs the steps (below), writes --dump-outputs if given and prints ONE JSON line: metric, value,
+ms_per_step, config.  --full then runs every other leg as well (the objects below, `value_cold`, and at N > 1 `ba_strong`)
+and prints the compact headline of them all, every leg in full going to bench_details.json and stderr.
 
 N > 1: one rank per GPU.  `python bench.py --gpus N` starts its own ranks (child `python -m torch.distributed.run`, the
 parent never touches the GPU) unless it already runs under torch.distributed.run (WORLD_SIZE set).  Landmarks shard
@@ -20,7 +24,7 @@ issued from C on the kernels' stream (mqs_ba_gn_iteration_dev; `transport` in th
 At N > 1 the weak run also reports configs[3] as `ba_strong`: the 1e6-landmark problem sharded N-way, 10 GN iterations,
 with the poses checked against the same problem solved by ONE rank (<= 1e-10).
 
-Extra objects on the JSON line:
+Extra objects on the JSON line under --full:
   roofline     -- the step's dominant kernel, the BA lineariser (`ba_linearize_wave_kernel<4, true>`, 0.55 of the step): counted
                   fp64 flop per launch / average launch duration from hipEvents on the launch stream against the 78.6 TFLOP/s
                   fp64 vector peak (what binds it), with the HBM view of the same launch (`roofline.hbm`: algorithmic bytes and
@@ -227,6 +231,29 @@ def headline(out, details_path):
     return h
 
 
+DUMP_ROWS = 1 << 18                 # landmarks per array in a --dump-outputs file: 3 x 6.3 MB + 2 MB + 1 MB in all at most
+
+
+def dump_outputs(path, x_ls, x_it, st, ba, rows=DUMP_ROWS, seed=2024):
+    """--dump-outputs: what the timed step hands its caller after its last step, as path/<name>.npy (rank 0's arrays):
+    linear_ls_points / iterative_ls_points (N, 3) f64 and iterative_ls_status (N,) as f32 from the triangulation pass, and
+    from the Gauss-Newton iteration ba_poses (C, 12) f64 and ba_points (N, 3) f64.  Past `rows` landmarks every per-landmark
+    array holds the same fixed, seeded, sorted sample of rows, whose indices are landmark_index (f64, exact)."""
+    import numpy as np
+    import torch
+    n = x_it.shape[0]
+    idx = np.arange(n) if n <= rows else np.sort(np.random.default_rng(seed).choice(n, rows, replace=False))
+    sel = torch.from_numpy(idx).to(x_it.device)
+    arrays = {"landmark_index": idx.astype(np.float64),
+              "linear_ls_points": x_ls[sel].double(), "iterative_ls_points": x_it[sel].double(), "iterative_ls_status": st[sel].float()}
+    if ba is not None:
+        arrays["ba_poses"] = ba.poses.double()
+        arrays["ba_points"] = ba.points[sel].double()
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a if isinstance(a, np.ndarray) else a.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -248,6 +275,12 @@ def main():
     ap.add_argument("--descriptors", type=int, default=65536)
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak")
     ap.add_argument("--strong-landmarks", type=int, default=1_000_000, help="total landmarks of the ba_strong leg (N > 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps, every other leg as well: the cold timed region, per-kernel timings and rooflines, "
+                         "the 1e7 asymptote, the BA reports, matcher, replay, front-end loops, sparse BA, CPU baselines and, at N > 1, "
+                         "ba_strong (the --no-* options trim this set); every leg in full goes to bench_details.json and stderr")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -266,7 +299,7 @@ def main():
 
     # everything that may need a compiler runs BEFORE the first GPU call (a child `make` started later would inherit an
     # initialised-GPU parent's profiler preload); both builders are no-ops when their library is up to date
-    want_cpu = (not args.no_cpu_baseline) and int(os.environ.get("WORLD_SIZE", "1")) == 1
+    want_cpu = args.full and (not args.no_cpu_baseline) and int(os.environ.get("WORLD_SIZE", "1")) == 1
     if want_cpu:
         from oracle import c_oracle
         c_oracle.build()
@@ -459,9 +492,15 @@ def main():
     #            clock over the first ~50-100 ms of sustained load: W = 5 warm-up steps end inside that ramp (0.223 against 0.199
     #            ms per step in round 2).  `value` / `ms_per_step` are the SETTLED figures -- the steady state a job that runs for
     #            more than a tenth of a second sees; `value_from` says so in the line and the cold figure stands beside it.
+    # The cold region is timed under --full only; a plain run issues the same K steps untimed, so that the settled figure and
+    # the BA state the timed steps leave (--dump-outputs) follow the same sequence of steps in both modes.
     for _ in range(args.warmup):
         step()
-    elapsed_cold = timed_steps(args.steps)
+    if args.full:
+        elapsed_cold = timed_steps(args.steps)
+    else:
+        for _ in range(args.steps):
+            step()
     for _ in range(args.settle_steps):
         step()
     fence()
@@ -471,6 +510,31 @@ def main():
 
     ms_per_step = 1e3 * elapsed / args.steps
     value = N_total / (elapsed / args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, x_ls, x_it, st, ba)
+    line = {
+        "metric": "triangulated landmarks/sec (linear-LS DLT + iterative-LS per landmark"
+                  + (" + 1 BA Gauss-Newton iteration" if ba is not None else "")
+                  + "), 1e6 pts x 4 cams per GPU; BA GN iters/sec in `ba`",
+        "value": round(value), "unit": "landmarks/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "clock_settle_steps": args.settle_steps, "ms_per_step": round(ms_per_step, 4),
+        "value_from": "ms_per_step: %d warm-up + %d timed steps after %d untimed clock-settling steps" % (args.warmup, args.steps, args.settle_steps),
+        "higher_is_better": True,
+        "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": ("BASELINE configs[3] shape: ONE scene of %d landmarks x %d cameras sharded %d-way, linear-LS + "
+                                "iterative-LS + 1 GN iteration per step" % (N_total, C, world)) if strong else
+                               ("BASELINE configs[1]: %d landmarks x %d cameras per GPU, linear-LS + "
+                                "iterative-LS (tol 3e-5, <=10 iterations)" % (N, C)),
+                   "landmarks_per_gpu": N, "landmarks_total": N_total, "cameras": C, "sharding": "landmarks, %d-way" % world},
+    }
+    if not args.full:
+        # a plain run: the headline and nothing else (every other leg: --full)
+        if rank == 0:
+            print(json.dumps(dict(line, transport=transport)), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     ms_per_step_cold = 1e3 * elapsed_cold / args.steps
     value_cold = N_total / (elapsed_cold / args.steps)
 
@@ -997,26 +1061,14 @@ def main():
                     transport += "; ba_strong over the RCCL all-reduce (%s)" % ("faster" if peer_ok else "the peer transport did not reproduce the one-rank poses")
 
     if rank == 0:
-        out = {
-            "metric": "triangulated landmarks/sec (linear-LS DLT + iterative-LS per landmark"
-                      + (" + 1 BA Gauss-Newton iteration" if ba is not None else "")
-                      + "), 1e6 pts x 4 cams per GPU; BA GN iters/sec in `ba`",
-            "value": round(value), "unit": "landmarks/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "clock_settle_steps": args.settle_steps, "ms_per_step": round(ms_per_step, 4),
+        out = dict(line, **{
             "ms_per_step_cold": round(ms_per_step_cold, 4), "value_cold": round(value_cold),
-            "value_from": "ms_per_step: %d warm-up + %d timed steps after %d untimed clock-settling steps; ms_per_step_cold / value_cold: "
-                          "the same %d + %d steps first thing in the process" % (args.warmup, args.steps, args.settle_steps, args.warmup, args.steps),
-            "higher_is_better": True,
-            "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": ("BASELINE configs[3] shape: ONE scene of %d landmarks x %d cameras sharded %d-way, linear-LS + "
-                                    "iterative-LS + 1 GN iteration per step" % (N_total, C, world)) if strong else
-                                   ("BASELINE configs[1]: %d landmarks x %d cameras per GPU, linear-LS + "
-                                    "iterative-LS (tol 3e-5, <=10 iterations)" % (N, C)),
-                       "landmarks_per_gpu": N, "landmarks_total": N_total, "cameras": C, "sharding": "landmarks, %d-way" % world},
+            "value_from": line["value_from"] + "; ms_per_step_cold / value_cold: the same %d + %d steps first thing in the process"
+                          % (args.warmup, args.steps),
             "transport": transport, "ba_strong": strong_out,
             "roofline": roofline, "rooflines": rooflines, "kernels": kernels, "asymptote": asymptote, "ba": ba_out, "match": match_out,
             "replay": replay_out, "frontend": frontend_out, "sparse_ba": sparse_out, "cpu_baseline": cpu,
-        }
+        })
         # The contract's ONE line on stdout is the compact headline (round 4's line had outgrown the driver's 8 KB tail: its head,
         # `value_cold` included, was cut); every leg in full goes to bench_details.json beside this file and, as one line, to stderr.
         details_path = os.path.join(ROOT, "bench_details.json")

@@ -95,9 +95,9 @@ def _bench_lines(r):
 
 @pytest.mark.parametrize("scaling", ["weak", "strong"])
 def test_bench_contract_two_ranks(gpu, tmp_path, scaling):
-    """Plain `python bench.py --gpus 2` (no launcher around it): the bench starts its own two ranks, rank 0 prints ONE
+    """`python bench.py --gpus 2 --full` (no launcher around it): the bench starts its own two ranks, rank 0 prints ONE
     line with n_gpus = 2, and the sharded configs[3] problem reproduces the one-rank poses (ba_strong.ok)."""
-    cmd = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--landmarks", "20000", "--strong-landmarks", "30001",
+    cmd = ["--gpus", "2", "--full", "--steps", "3", "--warmup", "1", "--landmarks", "20000", "--strong-landmarks", "30001",
            "--scaling", scaling, "--no-match", "--no-replay", "--no-frontend", "--no-cpu-baseline"]
     env = dict(os.environ, MQS_DIST_BACKEND="gloo", MQS_SHARED_GPU="1", MASTER_ADDR="127.0.0.1")
     env.pop("WORLD_SIZE", None)
@@ -123,9 +123,9 @@ def test_bench_contract_two_ranks(gpu, tmp_path, scaling):
 
 
 def test_bench_contract_single_gpu(gpu):
-    """`python bench.py` (N = 1) at a reduced size: ONE JSON line with the contract's keys, the roofline object of the
+    """`python bench.py --full` (N = 1) at a reduced size: ONE JSON line with the contract's keys, the roofline object of the
     dominant kernel and the CPU baseline timed beside it."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--landmarks", "50000",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--landmarks", "50000",
                         "--descriptors", "4096", "--no-replay", "--no-frontend"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     head, out = _bench_lines(r)
@@ -148,6 +148,41 @@ def test_bench_contract_single_gpu(gpu):
     assert cb["parity"]["rel_err_p99.9"] < 1e-5 and cb["parity"]["status_mismatch_frac"] < 0.005
     assert out["match"]["packed_bits_fp4"]["equals_fp16_path"] is True
     assert out["match"]["cross_match_4_cameras"]["pairs_this_rank"] == 6
+
+
+def test_bench_plain_run_and_dump_outputs(gpu, tmp_path):
+    """A plain `python bench.py` (no --full): ONE line with the headline keys and none of the --full legs, and --dump-outputs
+    writes the last step's arrays on a fixed sample of rows: the triangulation pass equal to the same pass run here on the
+    same seeded scene, the BA estimate finite."""
+    import torch
+    N, dump = 300000, tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--landmarks", str(N),
+                        "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    head = json.loads(lines[0])
+    for key, val in (("n_gpus", 1), ("steps", 4), ("warmup", 1), ("higher_is_better", True), ("scaling", "weak"), ("dtype", "f64"),
+                     ("data", "synthetic"), ("unit", "landmarks/s")):
+        assert head[key] == val, key
+    assert head["ms_per_step"] > 0 and head["value"] == pytest.approx(N / (head["ms_per_step"] * 1e-3), rel=1e-2)
+    assert "BA Gauss-Newton" in head["metric"] and head["config"]["landmarks_per_gpu"] == N
+    for key in ("value_cold", "roofline", "rooflines", "kernels", "cpu_baseline", "ba", "match", "loop", "frontend", "ba_strong"):
+        assert key not in head, key
+    files = {p.name[:-4]: np.load(p) for p in dump.iterdir()}
+    assert set(files) == {"landmark_index", "linear_ls_points", "iterative_ls_points", "iterative_ls_status", "ba_poses", "ba_points"}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(p.stat().st_size for p in dump.iterdir()) <= 64 << 20
+    idx = files["landmark_index"].astype(np.int64)
+    assert len(idx) == 1 << 18 and (np.diff(idx) > 0).all() and idx[-1] < N
+    syn = gpu.synthetic
+    u, P, _ = syn.triangulation_problem(N, 4, seed=syn.RSEED)
+    x_ls, x_it, st = gpu.device.linear_and_iterative_LS_triangulation(torch.from_numpy(u).cuda(), torch.from_numpy(np.ascontiguousarray(P)).cuda())
+    np.testing.assert_array_equal(files["linear_ls_points"], x_ls.cpu().numpy()[idx])
+    np.testing.assert_array_equal(files["iterative_ls_points"], x_it.cpu().numpy()[idx])
+    np.testing.assert_array_equal(files["iterative_ls_status"], st.cpu().numpy()[idx].astype(np.float32))
+    assert files["ba_poses"].shape == (4, 12) and np.isfinite(files["ba_poses"]).all()
+    assert files["ba_points"].shape == (1 << 18, 3) and np.isfinite(files["ba_points"]).all()
 
 
 def test_nccl_backend_plumbing_single_rank(gpu, tmp_path):
@@ -196,7 +231,7 @@ def test_bench_multi_gpu_code_path_on_the_real_backend(gpu):
     `python bench.py --gpus 8` runs."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MQS_DIST_BACKEND", "MQS_SHARED_GPU")}
     env.update(MQS_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(29900 + os.getpid() % 90))
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--landmarks", "20000",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--landmarks", "20000",
                         "--strong-landmarks", "30001", "--no-match", "--no-replay", "--no-frontend", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]

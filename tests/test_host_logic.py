@@ -39,3 +39,35 @@ def test_bench_headline_is_compact_and_complete():
     assert h["loop"]["cpu_baseline"] is None and h["loop"]["cpu_baseline_note"]
     assert h["asymptote_1e7"]["linear_ls_GBps"] == 5600.0 and h["asymptote_1e7"]["ba_ms_per_iter"] == 1.17
     assert len(h["transport"]) <= 160 and h["details"] == "stderr"
+
+
+def test_bench_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """bench.py --dump-outputs at the headline size (1e6 landmarks x 4 cameras): float arrays only, 64 MB at most in all, and the
+    same seeded sample of rows in every per-landmark array and from run to run."""
+    import importlib.util, os, types
+    import numpy as np
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    N = 1_000_000
+    rows = torch.arange(N, dtype=torch.float64)
+    x_ls, x_it = rows[:, None].repeat(1, 3), -rows[:, None].repeat(1, 3)
+    st = (torch.arange(N) % 3).to(torch.int32)
+    ba = types.SimpleNamespace(poses=torch.ones((4, 12), dtype=torch.float64), points=2 * x_ls)
+    got = []
+    for k in range(2):
+        d = tmp_path / str(k)
+        bench.dump_outputs(str(d), x_ls, x_it, st, ba)
+        got.append({p.name[:-4]: np.load(p) for p in d.iterdir()})
+        assert sum(p.stat().st_size for p in d.iterdir()) <= 64 << 20
+    a, b = got
+    assert set(a) == {"landmark_index", "linear_ls_points", "iterative_ls_points", "iterative_ls_status", "ba_poses", "ba_points"}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    idx = a["landmark_index"]
+    assert len(idx) == bench.DUMP_ROWS and (np.diff(idx) > 0).all() and idx[0] >= 0 and idx[-1] < N
+    assert np.array_equal(a["linear_ls_points"][:, 0], idx) and np.array_equal(a["iterative_ls_points"][:, 2], -idx)
+    assert np.array_equal(a["iterative_ls_status"], (idx % 3).astype(np.float32)) and np.array_equal(a["ba_points"][:, 1], 2 * idx)
+    assert a["ba_poses"].shape == (4, 12)

@@ -19,7 +19,7 @@ def leg(tag):
 leg("fresh")
 # what bench does before: the step legs
 import subprocess
-sys.argv = ["bench.py", "--no-frontend", "--no-cpu-baseline", "--no-asymptote", "--steps", "10", "--settle-steps", "10"]
+sys.argv = ["bench.py", "--full", "--no-frontend", "--no-cpu-baseline", "--no-asymptote", "--steps", "10", "--settle-steps", "10"]
 import runpy
 try:
     runpy.run_path("bench.py", run_name="__main__")

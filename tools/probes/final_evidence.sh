@@ -11,4 +11,4 @@ python tools/probes/loop_ba_seed_study.py 2>/dev/null > $OUT/loop_ba_seed_study.
 python tests/probe_icl_match_step.py 2>/dev/null | tail -4 > $OUT/match_step.txt
 python tools/probes/icl_ba_timing.py 2>/dev/null | tail -2 > $OUT/icl_ba_timing.txt
 bash tools/profile_loop_round.sh $OUT/loop_prof > /dev/null 2>&1
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err

@@ -15,5 +15,5 @@ find $OUT/kt_icl200 -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/
 python3 tools/pmc_summary.py $OUT/pmc_shape > $OUT/mfma_shape_mix_clock.json 2>/dev/null; rm -rf $OUT/pmc_shape
 ./tools/probes/mfma_shape_mix 2048 20 > $OUT/mfma_shape_mix.json
 bash tools/profile_round.sh $OUT/prof > /dev/null 2>&1
-python bench.py > $OUT/bench.json 2> $OUT/bench.err; cp bench_details.json $OUT/bench_details.json
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; cp bench_details.json $OUT/bench_details.json
 ls -la $OUT $OUT/prof $OUT/loop_prof

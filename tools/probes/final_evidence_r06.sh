@@ -19,5 +19,5 @@ timeout 900 bash tools/profile_round.sh $OUT/prof > /dev/null 2>&1
 ( cd /tmp && export TMPDIR=/tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/$OUT/kt_match" -- python3 "$ROOT/tools/ab_match.py" 65536 2 20 > "$ROOT/$OUT/matcher_under_rocprof.json" 2> /dev/null )
 find $OUT/kt_match -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/matcher_kernel_stats.csv; rm -rf $OUT/kt_match
 # 5. the bench line
-timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err; cp bench_details.json $OUT/bench_details.json
+timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; cp bench_details.json $OUT/bench_details.json
 ls -la $OUT $OUT/prof $OUT/loop_prof

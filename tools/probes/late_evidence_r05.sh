@@ -11,5 +11,5 @@ find $OUT/kt_icl200 -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/
 [ -f build/ab/libmqslam_stamps.so ] && MQS_LIB_PATH=build/ab/libmqslam_stamps.so python tools/probes/decide_phases.py 60 2>/dev/null | tail -1 > $OUT/decide_phases.json
 python tools/run_slam_loop.py 60 --device --repeats 3 2>/dev/null | tail -1 > $OUT/loop_plain.json
 python tools/run_slam_loop.py 60 --device --ba --reassociate --repeats 3 2>/dev/null | tail -1 > $OUT/loop_ba.json
-timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err; cp bench_details.json $OUT/bench_details.json
+timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; cp bench_details.json $OUT/bench_details.json
 ls -la $OUT $OUT/loop_prof
